@@ -111,7 +111,8 @@ enum {
     IPX_ERR_READ_TOO_LONG = -3, /* a read is longer than 4 096 bp (IPX_LONG_MAX_READ) */
     IPX_ERR_REF_TOO_LONG = -4,  /* a window is longer than 32 000 bp (IPX_MAX_REFLEN) */
     IPX_ERR_CIGAR_POOL = -5,    /* caller's cigar pool too small */
-    IPX_ERR_INTERNAL = -6
+    IPX_ERR_INTERNAL = -6,
+    IPX_ERR_EVENT_POOL = -7     /* caller's event pool too small (ipx_find_events) */
 };
 
 int ipx_device_count(void);
@@ -165,6 +166,31 @@ int ipx_pin_host(void *p, int64_t bytes);
 int ipx_unpin_host(void *p);
 int ipx_download_async(ipx_ctx *c, ipx_result *out, uint32_t *cigar_pool, int64_t cigar_cap, int64_t *n_cigar_ops);
 int ipx_wait(ipx_ctx *c);
+
+/* The event pass: every job's CIGAR decoded on the device as findall_indels decodes it (localn.pyx:542-621), its ops read
+ * through make_insertion_first (utilities.pyx:384-401, with merge_consecutive_gaps' end-of-list quirk).  One event per I / D
+ * token: ref_idx / read_idx are the window / read indices findall_indels has at that token, len its length.  With the letters
+ * also one 'X' event (len 1) per aligned base whose letters differ BYTE FOR BYTE, as the reference compares strings
+ * (localn.pyx:598): lower case, U and IUPAC letters count, which the int8 codes of the batch fold away.  Ops other than I / D
+ * advance read and window alike (codes above 8 read as M).  ssw.c's banded traceback can return a CIGAR one base longer than
+ * its read or window (ssw.c:734-751); past the end the walk goes on as the reference's string slices do: a base against no
+ * base is an 'X' event, no base against no base is none.  16 B. */
+typedef struct {
+    int32_t ref_idx;
+    int32_t read_idx;
+    int32_t len;
+    uint8_t kind;         /* 'I', 'D' or 'X' */
+    uint8_t pad[3];
+} ipx_event;
+
+/* After ipx_sync: the events of every job of the last run, in resident job order.  read_text / ref_text: the letters of the
+ * reads / windows at the offsets of the last ipx_upload (both given: 'X' events too; both NULL: indels only; one of them:
+ * IPX_ERR_ARG).  event_off / event_count: n_jobs each -- job j's events are events[event_off[j] .. + event_count[j]), in
+ * walk order (findall_indels' indels in CIGAR order, each run's mismatches in base order); a job without CIGAR has none.
+ * Pool too small: IPX_ERR_EVENT_POOL, *n_events = the size needed, caller buffers untouched.  A walk that starts at a
+ * negative index (never for a job with a CIGAR) or whose indices leave 32 bits: IPX_ERR_INTERNAL. */
+int ipx_find_events(ipx_ctx *c, const uint8_t *read_text, const uint8_t *ref_text, int64_t *event_off,
+                    int32_t *event_count, ipx_event *events, int64_t cap, int64_t *n_events);
 
 /* upload + run + sync + download in one call */
 int ipx_align_batch(ipx_ctx *c, const int8_t *reads, const int64_t *read_off, const int8_t *refs,

@@ -18,7 +18,7 @@ SRC = os.path.join(CSRC, "ipx_runtime.hip")
 # the library is several translation units (compiled in parallel): the runtime + every other kernel, and twenty
 # units holding the explicit instantiations of the striped-DP kernel families (csrc/ipx_kernels.h, end of file)
 UNITS = [SRC] + [os.path.join(CSRC, "ipx_dp_%s.hip" % u) for u in "abcdefghijklmnopqvwxyz"]
-HEADERS = [os.path.join(CSRC, h) for h in ("ipx_simt.h", "ipx_types.h", "ipx_kernels.h", "ipx_pipeline.h")] + [
+HEADERS = [os.path.join(CSRC, h) for h in ("ipx_simt.h", "ipx_types.h", "ipx_kernels.h", "ipx_pipeline.h", "ipx_events.h")] + [
     os.path.join(os.path.dirname(PKG_DIR), "include", "indelpost_hip.h")]
 BUILD_DIR = os.path.join(CSRC, "build")
 
@@ -29,6 +29,11 @@ RESULT_DTYPE = np.dtype([
     ("cigar_len", "<u2"), ("flag", "u1"), ("mode", "u1")])
 assert RESULT_DTYPE.itemsize == 32
 
+# numpy view of ipx_event (16 bytes): kind is b"I", b"D" or b"X"
+EVENT_DTYPE = np.dtype([("ref_idx", "<i4"), ("read_idx", "<i4"), ("len", "<i4"), ("kind", "S1"), ("pad", "V3")])
+assert EVENT_DTYPE.itemsize == 16
+IPX_ERR_ARG, IPX_ERR_INTERNAL, IPX_ERR_EVENT_POOL = -2, -6, -7
+
 EXPORTS = [
     # reference-compatible four-call interface (ssw.h:86,91,126-134,139)
     "ssw_init", "init_destroy", "ssw_align", "align_destroy",
@@ -38,6 +43,7 @@ EXPORTS = [
     "ipx_unpin_host", "ipx_align_batch", "ipx_set_profiling",
     "ipx_num_kernel_classes", "ipx_kernel_class_name", "ipx_kernel_times", "ipx_kernel_units", "ipx_last_run_ms", "ipx_debug_tb_counts", "ipx_debug_reruns",
     "ipx_synth_window", "ipx_synth_reads", "ipx_synth_mixed", "ipx_format_cigars", "ipx_cigar_hashes", "ipx_record_digest", "ipx_concat_sizes", "ipx_concat_tables", "ipx_group_by_length",
+    "ipx_find_events",
 ]
 
 
@@ -214,6 +220,8 @@ def load(path):
     L.ipx_group_by_length.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.ipx_synth_reads.restype = C.c_uint64
     L.ipx_synth_reads.argtypes = [C.c_uint64, vp, i32, vp, i64, i32]
+    L.ipx_find_events.restype = C.c_int
+    L.ipx_find_events.argtypes = [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.ipx_synth_mixed.restype = i64
     L.ipx_synth_mixed.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     for f in ("ipx_set_params", "ipx_set_routing", "ipx_upload", "ipx_run", "ipx_sync", "ipx_download", "ipx_download_async", "ipx_wait", "ipx_set_async_io", "ipx_pin_host",

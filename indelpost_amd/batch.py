@@ -11,7 +11,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import RESULT_DTYPE, IpxError
+from ._lib import EVENT_DTYPE, RESULT_DTYPE, IpxError
 
 _OPS = "MIDNSHP=X"
 
@@ -35,6 +35,15 @@ def encode_dna(seq):
     if isinstance(seq, str):
         seq = seq.encode("utf8")
     return DNA_LUT[np.frombuffer(seq, np.uint8)]
+
+
+def _letters(seq):
+    """str/bytes/array -> uint8 letters, byte for byte as encode_dna reads them (the strings as given, before encoding)"""
+    if isinstance(seq, np.ndarray):
+        return np.ascontiguousarray(seq).view(np.uint8).reshape(-1)
+    if isinstance(seq, str):
+        seq = seq.encode("utf8")
+    return np.frombuffer(bytes(seq), np.uint8)
 
 
 def dna_score_matrix(match_score, mismatch_penalty):
@@ -84,9 +93,27 @@ class JobTable:
     def n_refs(self):
         return len(self.ref_off) - 1
 
+    read_text = ref_text = None       # the letters of the reads / windows, same offsets as the codes (from_sequences(keep_text=True))
+
+    def text_table(self, read_text=None, ref_text=None):
+        """the job table with the LETTERS of its reads and windows in place of the codes (same offsets, windows and job
+        fields): cut and grouped by the same rules as the codes (shard, grouped_by_length), so that the letters of every
+        stream slice are what a slice's ipx_find_events reads.  Default: the letters the table keeps."""
+        rt = self.read_text if read_text is None else _letters(read_text)
+        ft = self.ref_text if ref_text is None else _letters(ref_text)
+        if rt is None or ft is None:
+            raise ValueError("the table keeps no letters (JobTable.from_sequences(..., keep_text=True))")
+        if len(rt) != int(self.read_off[-1]) or len(ft) != int(self.ref_off[-1]):
+            raise ValueError("letters of %d / %d bytes for a table of %d / %d" % (len(rt), len(ft), int(self.read_off[-1]), int(self.ref_off[-1])))
+        return JobTable(rt.view(np.int8), self.read_off, ft.view(np.int8), self.ref_off, self.ref_id, self.gap_open, self.gap_ext, self.mask_len)
+
     @classmethod
-    def from_sequences(cls, reads, refs, ref_id, gap_open, gap_ext, encoded=False):
-        """reads / refs: lists of str/bytes (or int8 arrays when encoded=True)."""
+    def from_sequences(cls, reads, refs, ref_id, gap_open, gap_ext, encoded=False, keep_text=False):
+        """reads / refs: lists of str/bytes (or int8 arrays when encoded=True).  keep_text: the table also keeps the letters
+        (read_text / ref_text, uint8, the strings as given) for the event pass (GpuAligner.find_events)."""
+        if keep_text and not encoded:
+            reads = [_letters(s) for s in reads]
+            refs = [_letters(s) for s in refs]
         enc = (lambda s: np.asarray(s, np.int8)) if encoded else encode_dna
         r = [enc(s) for s in reads]
         f = [enc(s) for s in refs]
@@ -98,7 +125,11 @@ class JobTable:
             fo[1:] = np.cumsum([len(x) for x in f])
         rc = np.concatenate(r) if r and ro[-1] else np.zeros(0, np.int8)
         fc = np.concatenate(f) if f and fo[-1] else np.zeros(0, np.int8)
-        return cls(rc, ro, fc, fo, ref_id, gap_open, gap_ext)
+        t = cls(rc, ro, fc, fo, ref_id, gap_open, gap_ext)
+        if keep_text and not encoded:
+            t.read_text = np.concatenate(reads) if reads and ro[-1] else np.zeros(0, np.uint8)
+            t.ref_text = np.concatenate(refs) if refs and fo[-1] else np.zeros(0, np.uint8)
+        return t
 
     def desc(self):
         """80 bytes = ten little-endian int64: addresses of reads, read_off, refs, ref_off, ref_id, gap_open, gap_ext, mask_len (or 0), then
@@ -462,6 +493,35 @@ class GpuAligner:
             self._check(rc, "ipx_align_batch")
             return BatchResult(rec, pool[:used.value])
 
+    def find_events(self, read_text=None, ref_text=None):
+        """After the batch's run (align(), or run() + sync()): the event pass of the library (ipx_find_events) over every job.
+        read_text / ref_text: the letters of the uploaded table's reads / windows at its offsets (JobTable.read_text /
+        ref_text), both or neither; with them the mismatching aligned bases come back too ('X' events).  Returns fresh arrays
+        (event_off int64, event_count int32, events EVENT_DTYPE): job j's events are events[event_off[j]:event_off[j] +
+        event_count[j]], in findall_indels' walk order."""
+        if (read_text is None) != (ref_text is None):
+            raise ValueError("find_events: the read and window letters go together (both or neither)")
+        n = self._n_jobs
+        jobs = getattr(self, "_jobs", None)
+        rt = ft = None
+        if read_text is not None:
+            rt, ft = _letters(read_text), _letters(ref_text)
+            if jobs is not None and (len(rt) != int(jobs.read_off[-1]) or len(ft) != int(jobs.ref_off[-1])):
+                raise ValueError("find_events: letters of %d / %d bytes for a batch of %d / %d" % (len(rt), len(ft), int(jobs.read_off[-1]), int(jobs.ref_off[-1])))
+        off, cnt = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        # every event is a gap token or an aligned base: read bytes + 8 per job is a bound the pass rarely comes near
+        # (np.empty commits no page it does not write)
+        cap = 8 * n + 64 + (len(rt) if rt is not None else 4 * n)
+        while True:
+            ev = np.empty(cap, EVENT_DTYPE)
+            used = C.c_int64(0)
+            rc = self._L.ipx_find_events(self._ctx, _p(rt), _p(ft), _p(off), _p(cnt), _p(ev), cap, C.byref(used))
+            if rc == _lib.IPX_ERR_EVENT_POOL and used.value > cap:
+                cap = int(used.value)
+                continue
+            self._check(rc, "ipx_find_events")
+            return off, cnt, ev[:used.value]
+
     # -- measurement --
     def set_profiling(self, on):
         # on: False/0 off, True/1 events around every launch, 2 only around the striped DP kernels
@@ -670,6 +730,7 @@ class MultiStreamAligner:
         the records in the caller's job order either way.  (submit() / align() -- a batch that passes through once -- do not: grouping a million
         jobs costs the host more than it saves the GPU.)"""
         self._order = None
+        table = jobs
         by_cells = self.balance_by_cells
         if self._worth_grouping(jobs):
             jobs, self._order = jobs.grouped_by_length()
@@ -677,6 +738,7 @@ class MultiStreamAligner:
         k = max(1, min(len(self.parts), jobs.n_jobs // self.min_jobs_per_stream))   # small batches: one stream
         b = shard_bounds(jobs.n_jobs, k, jobs if by_cells else None)
         self._active = self.parts[:k]
+        self._table, self._bounds = table, b
         self._slices = [jobs.shard(b[i], b[i + 1]) for i in range(k)]
         for p, j in zip(self._active, self._slices):
             p.upload(j)
@@ -732,6 +794,7 @@ class MultiStreamAligner:
         self._active = self.parts[:k]
         self._submitted = jobs
         self._order = None
+        self._table, self._bounds = jobs, b
 
         def one(i):                                                # cut, enqueue the copies of and launch slice i
             j = jobs.shard(b[i], b[i + 1])
@@ -786,6 +849,38 @@ class MultiStreamAligner:
             lo, n, pb = p._dl
             rec["cigar_off"][lo:lo + n] += np.uint32(pb)
         return BatchResult(rec, pool)
+
+    def find_events(self, read_text=None, ref_text=None):
+        """GpuAligner.find_events over the stream slices of the last batch, gathered into the CALLER's job order (the order of the
+        table given to upload / submit / align, also when upload grouped it by read length).  read_text / ref_text: the letters of
+        that table at its offsets (JobTable.read_text / ref_text), both or neither.  Fresh arrays (event_off, event_count,
+        events)."""
+        if (read_text is None) != (ref_text is None):
+            raise ValueError("find_events: the read and window letters go together (both or neither)")
+        parts, b = self._active, self._bounds
+        if read_text is None:
+            texts = [(None, None)] * len(parts)
+        else:
+            tt = self._table.text_table(read_text, ref_text)   # the letters cut (and grouped) exactly as the codes were
+            if self._order is not None:
+                tt = tt.grouped_by_length()[0]
+            texts = [(s_.reads.view(np.uint8), s_.refs.view(np.uint8)) for s_ in (tt.shard(b[i], b[i + 1]) for i in range(len(parts)))]
+        got = [p.find_events(r, f) for p, (r, f) in zip(parts, texts)]
+        if len(got) == 1:
+            off, cnt, ev = got[0]
+        else:
+            base, offs = 0, []
+            for o, c_, e in got:
+                offs.append(o + np.int64(base))
+                base += len(e)
+            off = np.concatenate(offs)
+            cnt = np.concatenate([g_[1] for g_ in got])
+            ev = np.concatenate([g_[2] for g_ in got])
+        if self._order is not None:                                # grouped by read length on the way in: back to the caller's order
+            o2, c2 = np.empty_like(off), np.empty_like(cnt)
+            o2[self._order], c2[self._order] = off, cnt
+            off, cnt = o2, c2
+        return off, cnt, ev
 
     def set_profiling(self, on):
         for p in self.parts:

@@ -15,6 +15,8 @@
 #include "../../include/indelpost_hip.h"
 #define IPX_EXTERN_KERNELS 1      // the k_dp_pass families are instantiated in csrc/ipx_dp_*.hip
 #include "ipx_pipeline.h"
+#include "ipx_events.h"
+static_assert(sizeof(IpxEvent) == 16 && sizeof(ipx_event) == 16, "event record is 16 bytes");
 
 static_assert(sizeof(IpxResult) == 32 && sizeof(ipx_result) == 32, "result record is 32 bytes");
 
@@ -76,6 +78,9 @@ struct ipx_ctx {
     DevBuf res, cigar_pool, small;     // small: cursor, status, plan tables, list counters
     DevBuf perm, tb_list, tb_esc, tb_bw, tb1, maxcol, tbf, long_state, rev;     // perm: three job lists of n_jobs (two static passes + one shared by the dynamic ones)
     uint32_t cigar_cap = 0;
+    int64_t read_bytes = 0, ref_bytes = 0;   // letters of the resident batch (ipx_find_events copies that many)
+    bool have_results = false;               // the last run of the resident batch completed (ipx_sync returned IPX_OK)
+    DevBuf evt_small, evt_off, evt_cnt, evt_pool, read_txt, ref_txt;   // event pass: cursor + status, per-job ranges, events, letters
     IpxWorkspace ws;
     IpxBatch batch;
     // measurement
@@ -263,7 +268,8 @@ void ipx_destroy(ipx_ctx *c)
     (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->reads, &c->read_off, &c->refs_raw, &c->ref_off, &c->refs_packed, &c->refp_off, &c->ref_len,
                       &c->ref_id, &c->gap_open, &c->gap_ext, &c->mask_len, &c->res, &c->cigar_pool, &c->small, &c->perm,
-                      &c->tb_list, &c->tb_esc, &c->tb_bw, &c->tb1, &c->maxcol, &c->tbf, &c->long_state, &c->rev})
+                      &c->tb_list, &c->tb_esc, &c->tb_bw, &c->tb1, &c->maxcol, &c->tbf, &c->long_state, &c->rev,
+                      &c->evt_small, &c->evt_off, &c->evt_cnt, &c->evt_pool, &c->read_txt, &c->ref_txt})
         b->release();
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipEventDestroy(c->run_start);
@@ -335,6 +341,7 @@ int ipx_upload(ipx_ctx *c, const int8_t *reads, const int64_t *read_off, const i
     c->static_valid = false;
     // launch sizes learned from the previous run only carry over to a batch of similar size
     if (c->prev_valid && (n_jobs > 2 * c->n_jobs || 2 * n_jobs < c->n_jobs)) c->prev_valid = false;
+    c->have_results = false;
     c->n_jobs = 0; c->n_refs = 0; c->batch.n_jobs = 0;           // (committed at the end, when every allocation and copy has been issued)
     c->have_mask = mask_len != nullptr;
 
@@ -483,6 +490,7 @@ int ipx_upload(ipx_ctx *c, const int8_t *reads, const int64_t *read_off, const i
     }
     if (!c->async_io) HIPCHK(hipStreamSynchronize(s));
     c->n_jobs = n_jobs; c->n_refs = n_refs;
+    c->read_bytes = read_bytes; c->ref_bytes = ref_bytes;
     return IPX_OK;
 }
 
@@ -490,6 +498,7 @@ static int ipx_run_impl(ipx_ctx *c, bool allow_speculation)
 {
     if (!c) { set_err("ipx_run: null context"); return IPX_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
+    c->have_results = false;
     IpxBatch &b = c->batch;
     memcpy(b.mat, c->mat, 25);
     b.word_first_len = (c->routing & IPX_ROUTE_NO_WORD_FIRST) ? 0 : ipx_word_first_len(c->mat, c->bias);
@@ -589,6 +598,7 @@ int ipx_sync(ipx_ctx *c)
     if (st & IPX_STATUS_TB_SCRATCH) { set_err("traceback scratch exhausted"); return IPX_ERR_INTERNAL; }
     if (st & IPX_STATUS_INTERNAL) { set_err("internal: a kernel variant met a job it was not built for"); return IPX_ERR_INTERNAL; }
     if (st & IPX_STATUS_RERUN) { set_err("internal: a job was left in a pass that did not run"); return IPX_ERR_INTERNAL; }
+    c->have_results = true;
     return IPX_OK;
 }
 
@@ -653,6 +663,68 @@ int ipx_wait(ipx_ctx *c)
     if (!c) { set_err("ipx_wait: null context"); return IPX_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return IPX_OK;
+}
+
+// The event pass over the last run (include/indelpost_hip.h): two lane-per-job launches on the context's stream -- k_events_count
+// sizes every job's range of the pool and reserves it, k_events_emit walks again and writes -- then one read-back.  Nothing is
+// written to the caller's buffers unless all of it fits.
+int ipx_find_events(ipx_ctx *c, const uint8_t *read_text, const uint8_t *ref_text, int64_t *event_off, int32_t *event_count,
+                    ipx_event *events, int64_t cap, int64_t *n_events)
+{
+    if (!c || !n_events || (read_text == nullptr) != (ref_text == nullptr) || cap < 0) {
+        set_err("ipx_find_events: bad argument (the read and window letters go together: both or neither)");
+        return IPX_ERR_ARG;
+    }
+    *n_events = 0;
+    if (c->n_jobs > 0 && (!c->have_results || c->runs_since_sync != 0)) { set_err("ipx_find_events: no completed run (ipx_run + ipx_sync first)"); return IPX_ERR_ARG; }
+    if (c->n_jobs == 0) return IPX_OK;
+    if (!event_off || !event_count) { set_err("ipx_find_events: bad argument"); return IPX_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = c->n_jobs;
+    const int letters = read_text != nullptr;
+    hipStream_t s = c->stream;
+    if (c->evt_small.ensure(64) || c->evt_off.ensure(8 * (size_t)n) || c->evt_cnt.ensure(4 * (size_t)n)) return IPX_ERR_NO_DEVICE;
+    if (letters) {
+        if (c->read_txt.ensure((size_t)c->read_bytes + 64) || c->ref_txt.ensure((size_t)c->ref_bytes + 64)) return IPX_ERR_NO_DEVICE;
+        if (c->read_bytes) HIPCHK(hipMemcpyAsync(c->read_txt.p, read_text, (size_t)c->read_bytes, hipMemcpyHostToDevice, s));
+        if (c->ref_bytes) HIPCHK(hipMemcpyAsync(c->ref_txt.p, ref_text, (size_t)c->ref_bytes, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemsetAsync(c->evt_small.p, 0, 16, s));                 // cursor, status
+    HIPCHK(hipMemsetAsync(c->evt_small.as<char>() + 16, 0xFF, 8, s));  // lowest job whose walk failed: none
+    const int block = 256;
+    int64_t g = (n + block - 1) / block;
+    if (g > (int64_t)c->num_cu * 16) g = (int64_t)c->num_cu * 16;
+    const IpxBatch &b = c->batch;
+    unsigned long long *cursor = c->evt_small.as<unsigned long long>();
+    uint32_t *status = (uint32_t *)(cursor + 1);
+    unsigned long long *first_bad = cursor + 2;
+    hipLaunchKernelGGL(k_events_count, dim3((unsigned)g), dim3(block), 0, s, (const IpxResult *)b.res, (const uint32_t *)b.cigar_pool,
+                       (const int64_t *)b.read_off, c->ref_off.as<const int64_t>(), (const int32_t *)b.ref_id, c->read_txt.as<const uint8_t>(),
+                       c->ref_txt.as<const uint8_t>(), letters, n, c->evt_off.as<int64_t>(), c->evt_cnt.as<int32_t>(), cursor, status, first_bad);
+    HIPCHK(hipGetLastError());
+    uint64_t back[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(back, c->evt_small.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((uint32_t)back[1]) { set_err("internal: the CIGAR walk of job %lld starts at a negative index or leaves 32-bit indices", (long long)back[2]); return IPX_ERR_INTERNAL; }
+    const int64_t total = (int64_t)back[0];
+    *n_events = total;
+    if (total > cap || (total > 0 && !events)) {
+        set_err("event pool of %lld events is too small, %lld needed", (long long)cap, (long long)total);
+        return IPX_ERR_EVENT_POOL;
+    }
+    if (total > 0) {
+        if (c->evt_pool.ensure(16 * (size_t)total)) return IPX_ERR_NO_DEVICE;
+        hipLaunchKernelGGL(k_events_emit, dim3((unsigned)g), dim3(block), 0, s, (const IpxResult *)b.res, (const uint32_t *)b.cigar_pool,
+                           (const int64_t *)b.read_off, c->ref_off.as<const int64_t>(), (const int32_t *)b.ref_id, c->read_txt.as<const uint8_t>(),
+                           c->ref_txt.as<const uint8_t>(), letters, n, c->evt_off.as<const int64_t>(), c->evt_cnt.as<const int32_t>(),
+                           c->evt_pool.as<IpxEvent>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(events, c->evt_pool.p, 16 * (size_t)total, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(event_off, c->evt_off.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(event_count, c->evt_cnt.p, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return IPX_OK;
 }
 

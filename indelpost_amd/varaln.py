@@ -4,6 +4,7 @@ Mirrors (citations into /root/reference/indelpost/varaln.pyx):
   generate_grid      :1122-1145  the (gap_open, gap_ext) pairs to try
   grid_search        :1148-1225  retarget under every pair, the best response's reads updated
   is_perfect_match   :1228-1234
+  decomposed_targets :122-143     the target selection of VariantAlignment.__cinit__, for many variants at once
 grid_search is where the reference spends its alignments: retarget once per pair (up to 7), each aligning every
 non-reference read against its own window, then update_read_info re-aligning the winning reads.  Here all pairs are ONE
 GPU batch per recursion level (pileup.retarget_many) and the winning reads reuse the alignments already made.
@@ -63,3 +64,40 @@ def is_perfect_match(aligner, contig_seq, read_seq):
     aligner.setRead(read_seq)
     a = aligner.align(gap_open=len(read_seq), gap_extension=len(read_seq))
     return contig_seq[a.reference_start:a.reference_end] == read_seq[a.read_start:a.read_end]
+
+
+def decomposed_targets(variants, match_score=3, mismatch_penalty=2, gap_open_penalty=3, gap_extension_penalty=1,
+                       auto_adjust_extension_penalty=True, device=0):
+    """varaln.pyx:122-143 for many targets: per variant (target, second_target, is_complex_input) as VariantAlignment.__cinit__
+    computes them.  A complex indel is decomposed -- with the default gaps when auto_adjust_extension_penalty is set, else with
+    the given ones -- and its decomposed indels, sorted stably by len(indel_seq), give the target (the last) and second_target
+    (the one before, when there are two or more; else the input).  Any other input gives target.normalize().  All complex
+    inputs of the call share ONE GPU batch (variant.decompose_each): the form a caller hands on to grid_search_many /
+    find_by_smith_waterman_realn_many.  Raises what the per-variant code raises, for the first variant in input order that fails."""
+    from .variant import decompose_each
+    variants = list(variants)
+    kinds = []                                             # per variant: True (complex input), False, or the exception of the test
+    for t in variants:
+        try:
+            kinds.append(not t.is_non_complex_indel() and t.is_indel)
+        except Exception as e:
+            kinds.append(e)
+            break
+    cx = [k for k, c in enumerate(kinds) if c is True]
+    gaps = () if auto_adjust_extension_penalty else (gap_open_penalty, gap_extension_penalty)
+    dec = dict(zip(cx, decompose_each([variants[k] for k in cx], match_score, mismatch_penalty, *gaps, device=device))) if cx else {}
+    out = []
+    for k, c in enumerate(kinds):
+        t = variants[k]
+        if isinstance(c, Exception):
+            raise c
+        if not c:
+            out.append((t.normalize(), t, False))
+            continue
+        d = dec[k]
+        if d is None or isinstance(d, Exception):
+            raise d if d is not None else RuntimeError("decomposition of %r did not run" % (t,))
+        indels = [i for i in d if i.is_indel]
+        indels.sort(key=lambda x: len(x.indel_seq))
+        out.append((indels[-1], indels[-2] if len(indels) > 1 else t, True))
+    return out

@@ -11,7 +11,7 @@ This is string logic around the hot path, outside SURVEY.md section 8's scope ta
 callers (retarget's candidate matching, the pileup front-end) need a Variant to hand back and to compare with.
 Parity: pinned by vectors produced by the reference's own class body executed as text (oracle/gen_variant_golden.py).
 """
-from .cigar import findall_indels, to_minimal_repeat_unit
+from .cigar import to_minimal_repeat_unit
 
 _BASES = set("ACTGNatcgn")
 
@@ -247,27 +247,68 @@ class Variant:
 
     def decompose_complex_variant(self, match_score=3, mismatch_penalty=2, gap_open_penalty=4, gap_extension_penalty=0):
         """the non-complex variants a complex one decomposes into under a Smith-Waterman alignment of the mutated against
-        the reference sequence, +-100 bases (variant.pyx:581-632)"""
-        if self.is_non_complex_indel():
-            return [self]
-        from .localn import align, make_aligner
-        v = self.normalize()
-        flank = 100
-        left_end = v.pos - 1                                   # 0-based end of the left flank
-        right_start = left_end + len(v.ref)
-        fa, chrom = self.reference, v.chrom
-        upstream = fa.fetch(chrom, left_end - flank, left_end)
-        mutated = upstream + v.alt + fa.fetch(chrom, right_start, right_start + flank)
-        original = fa.fetch(chrom, left_end - flank, right_start + flank)
-        aln = align(make_aligner(original, match_score, mismatch_penalty), mutated, gap_open_penalty, gap_extension_penalty)
-        indels, snvs = findall_indels(aln, left_end + 1 - flank + aln.reference_start, original, mutated, report_snvs=True)
-        parts = []
-        for d in indels:
-            pad = d["lt_ref"][-1]
-            ref, alt = (pad + d["del_seq"], pad) if d["indel_type"] == "D" else (pad, pad + d["indel_seq"])
-            parts.append(self._clone(pos=d["pos"], ref=ref, alt=alt))
-        parts.extend(self._clone(pos=x["pos"], ref=x["ref"], alt=x["alt"]) for x in snvs)
-        return parts
+        the reference sequence, +-100 bases (variant.pyx:581-632): the one-variant call of decompose_complex_variants"""
+        return decompose_complex_variants([self], match_score, mismatch_penalty, gap_open_penalty, gap_extension_penalty)[0]
 
     def __repr__(self):
         return "Variant(%r, %d, %r, %r)" % (self.chrom, self.pos, self.ref, self.alt)
+
+
+_FLANK = 100                                               # variant.pyx:605
+
+
+def decompose_each(variants, match_score=3, mismatch_penalty=2, gap_open_penalty=4, gap_extension_penalty=0, device=0):
+    """[v.decompose_complex_variant(...) for v in variants] as far as that loop gets, with the complex ones aligned as ONE GPU batch
+    and decoded by one event pass (events.align_and_find_each).  Per variant: its list of Variants, or the exception its call
+    raises; after the first variant whose windows cannot even be built (the loop would stop there) the entries are None."""
+    from .events import align_and_find_each
+    variants = list(variants)
+    out = [None] * len(variants)
+    todo = []                                              # (k, left end of the variant, reference window, mutated window)
+    for k, v in enumerate(variants):
+        try:
+            if v.is_non_complex_indel():                   # variant.pyx:597-598: not aligned
+                out[k] = [v]
+                continue
+            w = v.normalize()
+            left_end = w.pos - 1                           # variant.pyx:600-607
+            right_start = left_end + len(w.ref)
+            fa, chrom = v.reference, w.chrom
+            mutated = fa.fetch(chrom, left_end - _FLANK, left_end) + w.alt + fa.fetch(chrom, right_start, right_start + _FLANK)
+            original = fa.fetch(chrom, left_end - _FLANK, right_start + _FLANK)
+            todo.append((k, left_end, original, mutated))
+        except Exception as e:                             # the loop raises here: nothing after it runs
+            out[k] = e
+            break
+    if not todo:
+        return out
+    got = align_and_find_each([t[3] for t in todo], [t[2] for t in todo], [t[1] + 1 - _FLANK for t in todo], gap_open_penalty,
+                              gap_extension_penalty, match_score, mismatch_penalty, report_snvs=True, device=device)
+    for (k, _, _, _), r in zip(todo, got):
+        if isinstance(r, Exception):
+            out[k] = r
+            continue
+        v, (indels, snvs) = variants[k], r[1]
+        try:                                               # variant.pyx:615-632
+            parts = []
+            for d in indels:
+                pad = d["lt_ref"][-1]
+                ref, alt = (pad + d["del_seq"], pad) if d["indel_type"] == "D" else (pad, pad + d["indel_seq"])
+                parts.append(v._clone(pos=d["pos"], ref=ref, alt=alt))
+            parts.extend(v._clone(pos=x["pos"], ref=x["ref"], alt=x["alt"]) for x in snvs)
+            out[k] = parts
+        except Exception as e:
+            out[k] = e
+    return out
+
+
+def decompose_complex_variants(variants, match_score=3, mismatch_penalty=2, gap_open_penalty=4, gap_extension_penalty=0, device=0):
+    """exactly [v.decompose_complex_variant(match_score, mismatch_penalty, gap_open_penalty, gap_extension_penalty) for v in variants]
+    (variant.pyx:581-632), with every complex variant of the call in ONE GPU alignment batch and one event pass instead of one
+    alignment per variant.  Non-complex indels come back as [v] and are not aligned; the windows are fetched through each
+    variant's FASTA duck type as the method does.  Raises what the loop raises, for the first variant in input order that fails."""
+    out = decompose_each(variants, match_score, mismatch_penalty, gap_open_penalty, gap_extension_penalty, device)
+    for r in out:
+        if isinstance(r, Exception):
+            raise r
+    return out
